@@ -11,8 +11,13 @@ weights; when N > 1 the step includes the data-parallel gradient all-reduce (RCC
 patch-embedding backward.  Optimizer excluded (the north star names fwd+bwd).  Weak scaling:
 per-GPU batch fixed, `value` = images/s summed over all GPUs.
 
-Timed region: W warm-up steps, then barrier + torch.cuda.synchronize(), exactly K steps,
-synchronize + barrier; the time is the MAX over ranks.  Rank 0 prints ONE JSON line.
+Timed region: W warm-up steps, then barrier + torch.cuda.synchronize(), exactly K steps back to back, synchronize + barrier.
+HIP events on the stream split the K steps into (at most) `--repeats` windows; a window's time is the MAX over ranks and
+`ms_per_step` is the median window's time per step.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the LAST timed step handed its caller as DIR/<name>.npy (float32):
+`logits`, `loss` and `grad.<parameter name>` for every parameter, within 60 MB in all (see capture_outputs).  Weights, images and
+labels come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 
 Extra objects in the line:
   roofline      the step's large GEMMs are timed by CLASS on the launches of real training steps (every C-ABI call bracketed by HIP
@@ -237,19 +242,16 @@ def bench_navit(args, dev):
     def step():
         m.zero_grad(set_to_none=True)
         out = m(imgs, group_images=True, group_max_seq_len=4096)
-        torch.nn.functional.cross_entropy(out.float(), labels).backward()
+        loss = torch.nn.functional.cross_entropy(out.float(), labels)
+        loss.backward()
+        return out, loss
 
     for _ in range(args.warmup):
         step()
-    dts = []
-    for _ in range(max(1, args.repeats)):
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize(dev)
-        dts.append(time.perf_counter() - t0)
-    dt = sorted(dts)[len(dts) // 2] / args.steps
+    per_step, (out, loss) = run_timed(step, args.steps, args.repeats, lambda: torch.cuda.synchronize(dev))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, capture_outputs(out, loss, m))
+    dt = sorted(per_step)[len(per_step) // 2]
     lens = [(h // 16) * (w // 16) for h, w in sizes]
     gemm = depth * tok * (2 * D * 3 * I + 2 * I * D + 4 * D * F)
     attn = depth * sum(4 * H * n * n * 64 for n in lens)
@@ -257,7 +259,7 @@ def bench_navit(args, dev):
     print(json.dumps({
         "metric": "tokens/sec (fwd+bwd) NaViT packed variable-resolution batch, bf16", "value": round(tok / dt, 1), "unit": "tokens/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3),
-        "ms_per_step_all": [round(d / args.steps * 1e3, 3) for d in dts], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ms_per_step_all": [round(d * 1e3, 3) for d in per_step], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "bf16", "data": "synthetic (randn images of random sizes, randint labels, random-init weights)",
         "config": {"workload": f"navit dim {D} depth {depth} heads {H} mlp {F}: {len(imgs)} images of 64-640 px, {tok} tokens, packs of <= 4096 tokens, "
                                "cross-entropy loss, no optimizer", "images": len(imgs), "tokens": tok, "max_tokens_per_image": max(lens), "parallelism": "dp1"},
@@ -265,6 +267,59 @@ def bench_navit(args, dev):
         "model": {"tflops_per_gpu": round(tf, 2), "frac_of_mfma_peak": round(tf / PEAK_BF16_TFLOPS, 4),
                   "attention_share_of_flops": round(attn / (gemm + attn), 4)},
     }), flush=True)
+
+
+def timed_windows(steps: int, repeats: int):
+    """The K timed steps split into (at most) `repeats` back-to-back windows of near-equal length: K steps are timed in all."""
+    r = max(1, min(repeats, steps))
+    return [steps // r + (i < steps % r) for i in range(r)]
+
+
+def run_timed(step, steps: int, repeats: int, sync):
+    """The K timed steps back to back between one sync() pair, with HIP events on the current stream at the boundaries of the
+    windows of timed_windows() (no synchronisation between windows: the GPU never drains inside the timed region).  Every step's
+    work ends on the current stream (side streams are joined into it), so a window's event time is its steps' device time.
+    Returns (seconds per step of every window, what the last step returned)."""
+    wins = timed_windows(steps, repeats)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(len(wins) + 1)]
+    sync()
+    marks[0].record()
+    for i, n in enumerate(wins):
+        for _ in range(n):
+            ret = step()
+        marks[i + 1].record()
+    sync()
+    return [marks[i].elapsed_time(marks[i + 1]) * 1e-3 / n for i, n in enumerate(wins)], ret
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # the data; the .npy headers add a few kB
+
+
+def capture_outputs(logits, loss, model):
+    """What a caller of the timed step receives from it -- the logits, the loss and every parameter's gradient -- as float32 host
+    arrays within DUMP_BUDGET_BYTES.  Logits and loss are whole; every gradient is whole too unless the set would not fit, in which
+    case the gradients above a per-tensor cap keep only a fixed sample of their flat positions (oracle/params.py::sample_index, the
+    stride walk of the compact goldens), the cap halved until the set fits.  Same arguments, same positions."""
+    import numpy as np
+    from oracle.params import sample_index
+    out = {"logits": logits.detach().float().cpu().numpy(), "loss": np.asarray(loss.detach().float().cpu().numpy(), dtype=np.float32)}
+    grads = [(n, p.grad.detach()) for n, p in model.named_parameters() if p.grad is not None]
+    left = DUMP_BUDGET_BYTES - sum(a.nbytes for a in out.values())
+    cap = max((g.numel() for _, g in grads), default=0)
+    while cap > 1 and 4 * sum(min(g.numel(), cap) for _, g in grads) > left:
+        cap //= 2
+    for n, g in grads:
+        if g.numel() > cap:
+            g = g.flatten()[torch.from_numpy(sample_index(g.numel(), cap)).to(g.device)]
+        out["grad." + n] = g.float().cpu().numpy()
+    return out
+
+
+def write_outputs(dirpath: str, arrays):
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def box_calibration(dev):
@@ -371,9 +426,14 @@ def main():
                          "layer, e5m2 gradients for its four dX and four dW GEMMs; attention and LayerNorm stay bf16.  Same as "
                          "--precision fp8.  VITK_FP8_K128=0 selects the K = 32 MFMA forms (default: K = 128).  Not the headline metric (that one is bf16).")
     ap.add_argument("--repeats", type=int, default=3,
-                    help="time the K-step region this many times and report the MEDIAN window (every repeat is exactly K steps "
-                         "between barrier + synchronize; all of them are listed in ms_per_step_all)")
+                    help="split the K timed steps (run back to back) into this many windows timed by HIP events and report the "
+                         "MEDIAN window's time per step; every window's is listed in ms_per_step_all")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's logits, loss and parameter gradients as DIR/<name>.npy "
+                         "(float32, at most 60 MB in all; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -419,7 +479,7 @@ def main():
         logits = dp(img)
         loss = torch.nn.functional.cross_entropy(logits.float(), labels)
         dp.backward(loss)  # zeroes .grad, backward, overlapped all-reduce when world > 1
-        return loss
+        return logits, loss
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -431,28 +491,22 @@ def main():
     for _ in range(args.warmup):
         step()
     # Shared GPU boxes show occasional multi-x slow phases (clock / power state; one measured run: 100.9, 39.6, 39.6 ms);
-    # one such phase inside a single 20-step window would misreport the kernel work, so the window is repeated and the
-    # median window reported (all windows are in ms_per_step_all).
-    dts, rank_dts = [], []
-    for _ in range(max(1, args.repeats)):
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loss = step()
-        sync()
-        dt = time.perf_counter() - t0
-        if world > 1:
-            t = torch.tensor([dt], device=dev, dtype=torch.float64)
-            every = [torch.empty_like(t) for _ in range(world)]
-            dist.all_gather(every, t)
-            rank_dts.append([float(e.item()) for e in every])
-            dt = max(rank_dts[-1])                   # the step is as slow as its slowest rank
-        else:
-            rank_dts.append([dt])
-        dts.append(dt)
+    # one such phase inside a single window would misreport the kernel work, so the K timed steps are split into windows and
+    # the median window reported (all windows are in ms_per_step_all).
+    per_step, (logits, loss) = run_timed(step, args.steps, args.repeats, sync)
+    if world > 1:
+        t = torch.tensor(per_step, device=dev, dtype=torch.float64)
+        every = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(every, t)
+        rank_dts = [[float(e[i].item()) for e in every] for i in range(len(per_step))]
+    else:
+        rank_dts = [[d] for d in per_step]
+    dts = [max(r) for r in rank_dts]                 # the step is as slow as its slowest rank
     mid = sorted(range(len(dts)), key=dts.__getitem__)[len(dts) // 2]
     dt = dts[mid]
     assert torch.isfinite(loss).item(), "loss is not finite"
+    if args.dump_outputs and rank == 0:      # before any later step overwrites the gradient buffer
+        write_outputs(args.dump_outputs, capture_outputs(logits, loss, model))
     comm_stats = None
     if world > 1:       # one more step with the collectives timed (HIP events on the communication stream) -- after the timed region
         dp.sink.enable_timing(True)
@@ -480,9 +534,8 @@ def main():
     weight_cache_rebuild_ms = sorted(rebuild)[1]
 
     if rank == 0:
-        ms = dt / args.steps * 1e3
-        total_imgs = batch * world * args.steps
-        value = total_imgs / dt
+        ms = dt * 1e3
+        value = batch * world / dt
         gf = 3.0 * fwd_gflop_per_image(cfg)
         N = (cfg["image_size"] // cfg["patch_size"]) ** 2 + 1
         k128 = bool(args.fp8 and model.transformer._fp8.k128)
@@ -537,7 +590,7 @@ def main():
         line = {
             "metric": "images/sec (fwd+bwd) ViT-B/16 224^2 bf16" if (args.config == "vit_b16" and not args.fp8) else f"images/sec (fwd+bwd) {args.config} {prec}",
             "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms, 3), "ms_per_step_all": [round(d / args.steps * 1e3, 3) for d in dts],
+            "ms_per_step": round(ms, 3), "ms_per_step_all": [round(d * 1e3, 3) for d in dts],
             "weight_cache_rebuild_ms": round(weight_cache_rebuild_ms, 3),
             "train_loop_ms_per_step": round(ms + weight_cache_rebuild_ms, 3),      # fwd+bwd inside a loop whose optimizer changes the weights every step
             "train_loop_images_per_s": round(batch * world / ((ms + weight_cache_rebuild_ms) * 1e-3), 2),
@@ -555,7 +608,7 @@ def main():
                                    + (", flat-buffer RCCL all-reduce overlapped with patch-embed backward" if world > 1 else ""),
                        "global_batch": batch * world, "per_gpu_batch": batch, "seq_len": N, "parallelism": f"dp{world}"},
             "per_gpu_images_per_s": round(value / world, 2),
-            "per_rank_images_per_s": [round(batch * args.steps / d, 2) for d in rank_dts[mid]],       # each rank's own clock, the reported window
+            "per_rank_images_per_s": [round(batch / d, 2) for d in rank_dts[mid]],       # each rank's own clock, the reported window
             "device_count": torch.cuda.device_count(), "rccl_version": rccl_version(),
             **({"comm": {**comm_stats, "process_group_world": dist.get_world_size(),
                          "note": "one extra step after the timed region: bytes and event-timed duration of each gradient all-reduce on the "

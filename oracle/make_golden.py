@@ -259,7 +259,67 @@ def main_navit_bench():
         print(f"{name}: {len(sizes)} images, logits {tuple(out.shape)} {len(grads)} grads -> {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
 
 
+FUZZ_GOLDEN = "fuzz_draws"
+FUZZ_SAMPLE = 64            # entries stored per gradient tensor (sample_index; smaller tensors are stored whole)
+FUZZ_LOGITS_SAMPLE = 1024   # entries stored per output (sample_index; smaller outputs are stored whole)
+FUZZ_NAVIT_DRAWS = 8
+
+
+def _fuzz_record(blob, tag, out, grads, out16=None):
+    """One draw into `blob`: the output's sampled entries (`<tag>::logits`, and `<tag>::bf16::logits` at the same positions), every
+    gradient's sampled entries concatenated in `grads`' order (`<tag>::gsample`).  Returns the draw's layout for the JSON index."""
+    idx = sample_index(out.numel(), FUZZ_LOGITS_SAMPLE)
+    blob[f"{tag}::logits"] = out.detach().flatten().numpy()[idx]
+    if out16 is not None:
+        blob[f"{tag}::bf16::logits"] = out16.detach().float().flatten().numpy()[idx]
+    blob[f"{tag}::gsample"] = np.concatenate([g.detach().flatten().numpy()[sample_index(g.numel(), FUZZ_SAMPLE)] for g in grads.values()])
+    return {"logits_shape": list(out.shape), "grads": [[k, g.numel()] for k, g in grads.items()]}
+
+
+def main_fuzz():
+    """The reference on the seeded random configurations of the GPU fuzz tests (tests/test_fuzz_gpu.py::draw / draw_navit), one compact
+    file tests/golden/fuzz_draws.npz that tests/test_oracle_fuzz_vs_reference.py holds the oracle against.  Per ViT / SimpleViT draw
+    `<seed>::...` and per NaViT draw `navit<seed>::...` (see _fuzz_record): a fixed sample of the f32 output, of every gradient and,
+    on every fourth ViT / SimpleViT draw, of the output of the reference's own pure-bf16 run.  `draws` (JSON) records every draw's
+    configuration, output shape and gradient layout, so that a changed draw function shows up as a stale golden instead of a silent
+    mismatch."""
+    import json
+    if ONLY and FUZZ_GOLDEN not in ONLY:
+        return
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import test_fuzz_gpu as F
+    torch.set_num_threads(min(8, os.cpu_count() or 1))
+    outdir = os.path.join(os.path.dirname(HERE), "tests", "golden")
+    blob, draws = {}, {}
+    for seed in range(F.N_DRAWS):
+        kind, cfg, batch = F.draw(seed)
+        params = make_params(kind, cfg, 50 + seed)
+        img = make_images(cfg, batch, 1050 + seed)
+        out, _, grads = run_reference(kind, cfg, params, img)
+        out16 = run_reference(kind, cfg, params, img, torch.bfloat16)[0] if seed % 4 == 0 else None
+        draws[str(seed)] = {"draw": [kind, cfg, batch], **_fuzz_record(blob, str(seed), out, grads, out16)}
+    mod = load_ref("na_vit")
+    for seed in range(FUZZ_NAVIT_DRAWS):
+        cfg, packs = F.draw_navit(seed)
+        params = make_navit_params(cfg, 90 + seed)
+        images = make_navit_images(cfg, packs, 1090 + seed)
+        model = mod.NaViT(**cfg)
+        model.load_state_dict(params, strict=True)
+        model.eval()
+        out = model(images)
+        loss_fn(out).backward()
+        grads = {k: (p.grad if p.grad is not None else torch.zeros_like(p)) for k, p in model.named_parameters()}
+        draws[f"navit{seed}"] = {"draw": [cfg, packs], **_fuzz_record(blob, f"navit{seed}", out, grads)}
+    blob["draws"] = np.frombuffer(json.dumps(draws, sort_keys=True).encode(), dtype=np.uint8)
+    path = os.path.join(outdir, FUZZ_GOLDEN + ".npz")
+    np.savez_compressed(path, **blob)
+    print(f"{FUZZ_GOLDEN}: {F.N_DRAWS} draws + {FUZZ_NAVIT_DRAWS} NaViT draws -> {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
 if __name__ == "__main__":
+    if ONLY == {FUZZ_GOLDEN}:
+        main_fuzz()
+        sys.exit(0)
     if ONLY and all(n in NAVIT_BENCH_CASES for n in ONLY):
         main_navit_bench()
         sys.exit(0)
@@ -273,3 +333,4 @@ if __name__ == "__main__":
     main_navit_wide()
     main_navit_bench()
     main_autocast()
+    main_fuzz()

@@ -1,45 +1,11 @@
 """Consumers of the encoder's internals: the reference's Recorder (recorder.py:26-29), Extractor
-(extractor.py:50-57) and Dino's NetWrapper (dino.py:134-151) wired around the drop-in modules.
+(extractor.py:50-57), Dino's NetWrapper (dino.py:134-151) and T2TViT (t2t.py:45, 57) wired around the drop-in modules.
 
-CPU part (runs where /root/reference exists, i.e. in the build container): the reference's OWN wrapper classes are imported with
-`vit_pytorch.vit` aliased to `vit_pytorch_amd.vit` and must find their hook points -- every `Attention.attend`, the `transformer`
-attribute, `children()[-2]` = `to_latent`.  GPU part: the same wiring restated (the reference does not travel to the GPU box),
-run end to end against the un-hooked fused path."""
-import importlib.util
-import os
-import sys
-import types
-
+CPU part: the hook points those wrappers look up, restated -- every `Attention.attend` under `transformer` (found by isinstance), the
+`transformer` attribute, `children()[-2]` = `to_latent`, and `Transformer` built with t2t.py's arguments -- must exist on the drop-in
+and take / release forward hooks.  GPU part: the same wiring run end to end against the un-hooked fused path."""
 import pytest
 import torch
-
-REF = "/root/reference/vit_pytorch"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists in the build container only")
-
-
-def _load_ref_module(name):
-    """Import /root/reference/vit_pytorch/<name>.py with `vit_pytorch.vit` resolving to the drop-in and torchvision stubbed."""
-    sys.dont_write_bytecode = True
-    import vit_pytorch_amd.vit as mine
-    pkg = types.ModuleType("vit_pytorch"); pkg.__path__ = []
-    saved = {k: sys.modules.get(k) for k in ("vit_pytorch", "vit_pytorch.vit", "torchvision", "torchvision.transforms")}
-    sys.modules["vit_pytorch"] = pkg
-    sys.modules["vit_pytorch.vit"] = mine
-    tv = types.ModuleType("torchvision"); tvt = types.ModuleType("torchvision.transforms")
-    tvt.__getattr__ = lambda attr: (lambda *a, **k: torch.nn.Identity())       # dino.py only builds augmentation pipelines from it
-    tv.transforms = tvt
-    sys.modules.setdefault("torchvision", tv); sys.modules.setdefault("torchvision.transforms", tvt)
-    try:
-        spec = importlib.util.spec_from_file_location(f"_ref_consumer_{name}", os.path.join(REF, f"{name}.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
 
 
 def _tiny_vit():
@@ -47,33 +13,51 @@ def _tiny_vit():
     return ViT(image_size=32, patch_size=8, num_classes=5, dim=32, depth=3, heads=2, dim_head=16, mlp_dim=64)
 
 
-@needs_ref
 def test_reference_recorder_finds_every_attend_module():
-    rec_mod = _load_ref_module("recorder")
-    v = _tiny_vit()
-    rec = rec_mod.Recorder(v)
-    rec._register_hook()                                  # recorder.py:26-31
-    assert rec.hook_registered and len(rec.hooks) == 3
+    """recorder.py:7-8, 26-31: every module of `vit.transformer` that is an `Attention` gets a forward hook on its `attend`; eject
+    (recorder.py:33-38) removes them and hands back the model."""
     from vit_pytorch_amd.vit import Attention
+    v = _tiny_vit()
+    hooks = [m.attend.register_forward_hook(lambda *_: None) for m in v.transformer.modules() if isinstance(m, Attention)]
+    assert len(hooks) == 3
     attends = [m.attend for m in v.transformer.modules() if isinstance(m, Attention)]
     assert len(attends) == 3 and all(len(a._forward_hooks) == 1 for a in attends)
-    assert rec.eject() is v and all(len(a._forward_hooks) == 0 for a in attends)
+    for h in hooks:
+        h.remove()
+    assert all(len(a._forward_hooks) == 0 for a in attends)
 
 
-@needs_ref
 def test_reference_extractor_and_netwrapper_find_their_layers():
-    ext_mod = _load_ref_module("extractor")
+    """extractor.py:50-59: a forward hook on the `transformer` attribute; dino.py:134-140 with layer = -2: `children()[-2]`."""
     v = _tiny_vit()
-    ext = ext_mod.Extractor(v)
-    ext._register_hook()                                  # extractor.py:50-59: the `transformer` attribute
+    assert hasattr(v, "transformer")
+    h = v.transformer.register_forward_hook(lambda *_: None)
     assert len(v.transformer._forward_hooks) == 1
-    ext.eject()
-    dino = _load_ref_module("dino")
-    w = dino.NetWrapper(v, output_dim=16, projection_hidden_size=32, projection_num_layers=2, layer=-2)
-    assert w._find_layer() is v.to_latent                 # dino.py:138-140: children()[-2]
+    h.remove()
+    assert len(v.transformer._forward_hooks) == 0
+    assert [*v.children()][-2] is v.to_latent
     from vit_pytorch_amd import SimpleViT
     s = SimpleViT(image_size=32, patch_size=8, num_classes=5, dim=32, depth=1, heads=2, dim_head=16, mlp_dim=64)
-    assert dino.NetWrapper(s, 16, 32, 2, layer=-2)._find_layer() is s.to_latent
+    assert [*s.children()][-2] is s.to_latent
+
+
+def test_reference_t2t_vit_builds_on_the_drop_in_transformer():
+    """t2t.py:5 imports vit_pytorch.vit.Transformer.  T2TViT(image_size=64, dim=64, depth=2, heads=2, mlp_dim=128) with its default
+    t2t_layers ((7, 4), (3, 2), (3, 2)) and 3 channels builds two token-to-token layers by keyword (t2t.py:45: dim = heads' width =
+    mlp_dim = 3 * 7 * 7 = 147 and 147 * 3 * 3 = 1323, heads = 1, depth = 1; the third t2t layer is an Identity) and its main
+    transformer POSITIONALLY (t2t.py:57: Transformer(dim, depth, heads, dim_head, mlp_dim, dropout)) -- the drop-in must accept both."""
+    import vit_pytorch_amd.vit as mine
+    channels, ts = 3, []
+    for i, (kernel, _stride) in enumerate(((7, 4), (3, 2), (3, 2))):
+        channels *= kernel ** 2
+        if i < 2:
+            ts.append(mine.Transformer(dim=channels, heads=1, depth=1, dim_head=channels, mlp_dim=channels, dropout=0.))
+    ts.append(mine.Transformer(64, 2, 2, 64, 128, 0.))
+    assert all(isinstance(t, mine.Transformer) for t in ts)
+    assert sorted(t.norm.weight.shape[0] for t in ts) == [64, 147, 1323]
+    assert len(ts[2].layers) == 2
+    for t in ts[:2]:
+        assert isinstance(t.layers[0][0].to_out, torch.nn.Identity)      # heads == 1 and dim_head == dim (vit.py:45)
 
 
 # ---- GPU: the same wiring, end to end ------------------------------------------------------------------------------------
@@ -180,17 +164,3 @@ def test_t2t_width_in_bfloat16():
     (y.float() * r).sum().backward()
     ref, gref = _torch_block(t32, x, r, dim, 1, dim)
     assert _rel(y, ref) < 3e-2 and _rel(xb.grad, gref) < 6e-2, (_rel(y, ref), _rel(xb.grad, gref))
-
-
-@needs_ref
-def test_reference_t2t_vit_builds_on_the_drop_in_transformer():
-    """t2t.py:5 imports vit_pytorch.vit.Transformer; with the alias its token-to-token layers (t2t.py:45) and its main
-    transformer (t2t.py:57) are the drop-in's modules, including the 147- and 1323-wide ones."""
-    import vit_pytorch_amd.vit as mine
-    mod = _load_ref_module("t2t")
-    v = mod.T2TViT(image_size=64, num_classes=10, dim=64, depth=2, heads=2, mlp_dim=128)
-    ts = [m for m in v.modules() if isinstance(m, mine.Transformer)]
-    assert len(ts) == 3
-    assert sorted(t.norm.weight.shape[0] for t in ts) == [64, 147, 1323]
-    for t in ts[:2]:
-        assert isinstance(t.layers[0][0].to_out, torch.nn.Identity)      # heads == 1 and dim_head == dim (vit.py:45)
