@@ -164,6 +164,10 @@ int vitk_gemm_nt_bf16_mul_aux8_colsum(const void* A, int64_t lda, const void* W,
 /* Tile schedule of the persistent NT kernel for (M, N, K) (tests, tuning): out[0] = 1 when the shape is served by it,
  * out[1] = 256-row m-tiles, out[2] = 128-row m-tiles of the tail region, out[3] = resident workgroups, out[4] = n-tiles. */
 int vitk_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int64_t ldc, int32_t* out5);
+/* One-launch plan of the four-wave NT kernel on `grid` workgroups (used where M % 128 == 0 and the epilogue has no column sums):
+ * out4 = {256-row tiles, 128-row tiles, modelled makespan x 1000, the two-launch split's modelled cost x 1000} (units: one 256-row
+ * tile); all 0 where the shape takes the two-launch split. */
+int vitk_gemm_nt_w128_plan(int64_t M, int64_t N, int64_t K, int32_t grid, int32_t* out4);
 /* K-blocked copy of a weight for the persistent NT kernel (no reference counterpart: nn.Linear's weight, vit.py:20,23,44,47,
  * stays as it is; this is a derived cache like the transposed copy).  W is N x K row-major 16-bit.  `out` receives the operand
  * of y = x . W^T (rows N, reduction K; K % 32 == 0; vitk_pack_w_nt_bytes(N, K) bytes), `out_t` the operand of dX = dY . W

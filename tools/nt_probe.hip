@@ -21,6 +21,9 @@
 
 #define gemm_ntw_serves probe_ntw_serves
 #define gemm_ntw_split probe_ntw_split
+#define gemm_ntw_plan probe_ntw_plan
+#define gemm_ntw_half_cost probe_ntw_half_cost
+#define gemm_ntw_makespan probe_ntw_makespan
 #define gemm_ntw_launch probe_ntw_launch
 #include "../vit_pytorch_amd/csrc/gemm_nt_w128.hip"
 #define NTX_PROBE
@@ -142,10 +145,10 @@ int main(int argc, char** argv) {
                 else if (epi == VITK_EPI_GELU_BWD) VK(vitk_gemm_nt_bf16_gelu_bwd_colsum(A.p, K, Wp.p, 0, C.p, N, M, N, K, aux, (float*)cs.p, nullptr));
                 else VK(vitk_gemm_nt_bf16(A.p, K, Wp.p, 0, C.p, N, M, N, K, epi, has_bias ? bias.p : nullptr, (const float*)resid, aux, nullptr));
             };
-            auto direct = [&](int tiles_m, int abl, int dbg) {      // the four-wave launch alone
+            auto direct = [&](int tiles_m, int abl, int dbg, int tiles_mh = 0) {      // the four-wave launch alone
                 void* aux = aux_is_in ? aux_in.p : (aux_is_out ? X1.p : nullptr);
                 VK(probe_ntw_launch(tiles_m, grid, A.p, K, Wp.p, 0, C1.p, N, N, K, epi, has_bias ? bias.p : nullptr, resid, aux,
-                                    aux_is_in ? (float*)cs1.p : nullptr, abl, dbg, nullptr));
+                                    aux_is_in ? (float*)cs1.p : nullptr, abl, dbg, nullptr, tiles_mh));
             };
             // ---- parity: product path vs the 8-wave kernel alone, bit for bit ----
             CK(hipMemset(C0.p, 0xff, cbytes)); CK(hipMemset(C1.p, 0xee, cbytes));
@@ -214,6 +217,17 @@ int main(int argc, char** argv) {
                    epi_name[epi], mo * 1e3, flop / mo / 1e9, mn * 1e3, flop / mn / 1e9, mo / mn, tm_all, md * 1e3, 2.0 * 256 * tm_all * N * K / md / 1e9);
             printf("  %-13s    with round 5's 64-byte activation pieces (VITK_NTW_A128=0): product path %7.1f us (128-byte rows x%.3f) | four-wave kernel alone %7.1f us (x%.3f)\n",
                    epi_name[epi], m5 * 1e3, m5 / mn, md5 * 1e3, md5 / md);
+            if (!aux_is_in) {      // the cost of a 128-row tile against a 256-row one (gemm_ntw_half_cost): all rows as 128-row tiles
+                std::vector<float> t_full, t_half;
+                for (int r = 0; r <= rounds; ++r) {
+                    const float a = time_ms([&] { direct(tm_all, 0, 0); }, 10);
+                    const float b = time_ms([&] { direct(0, 0, 0, (int)(M / 128)); }, 10);
+                    if (r) { t_full.push_back(a); t_half.push_back(b); }
+                }
+                const float mf = median(t_full), mh = median(t_half);
+                printf("  %-13s four-wave kernel, all rows as 256-row tiles %7.1f us | as 128-row tiles %7.1f us: 128-row tile = %.3f x 256-row tile (model %.3f)\n",
+                       epi_name[epi], mf * 1e3, mh * 1e3, mh / (2.0 * mf), probe_ntw_half_cost(K));
+            }
             if (epi == sh.epis[0] || epi == VITK_EPI_RESID16 || epi == VITK_EPI_BIAS_GELU_DG8 || epi == VITK_EPI_MUL_AUX8) { sum_old += mo; sum_new += mn; }
             // ---- round 6: two wave groups of one workgroup swapping roles (csrc/gemm_nt_x2.hip): parity against the four-wave kernel alone, timing ----
             const bool x2_epi = epi == VITK_EPI_NONE || epi == VITK_EPI_BIAS_GELU_DG || epi == VITK_EPI_BIAS_GELU_DG8 || epi == VITK_EPI_MUL_AUX || epi == VITK_EPI_MUL_AUX8;

@@ -21,6 +21,9 @@
 
 #define gemm_ntw_serves probe_ntw_serves
 #define gemm_ntw_split probe_ntw_split
+#define gemm_ntw_plan probe_ntw_plan
+#define gemm_ntw_half_cost probe_ntw_half_cost
+#define gemm_ntw_makespan probe_ntw_makespan
 #define gemm_ntw_launch probe_ntw_launch
 #include "../vit_pytorch_amd/csrc/gemm_nt_w128.hip"
 #define gemm_ntd_serves probe_ntd_serves

@@ -76,6 +76,7 @@ SIGNATURES = {
     "vitk_gemm_tn_fp8": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i64, _i, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i, _vp]),
     "vitk_gemm_nt_colsum_rows": (_i64, [_i64, _i64, _i64, _i64]),
     "vitk_gemm_nt_plan": (_i, [_i64, _i64, _i64, _i64, _vp]),
+    "vitk_gemm_nt_w128_plan": (_i, [_i64, _i64, _i64, _i, _vp]),
     "vitk_comm_unique_id": (_i, [_vp]),
     "vitk_comm_init": (_i, [_vp, _i, _i, _vp]),
     "vitk_comm_allreduce": (_i, [_vp, _vp, _i64, _i, _i, _vp]),

@@ -829,6 +829,23 @@ extern "C" int vitk_gemm_nt_plan(int64_t M, int64_t N, int64_t K, int64_t ldc, i
     return 0;
 }
 
+extern "C" int vitk_gemm_nt_w128_plan(int64_t M, int64_t N, int64_t K, int32_t grid, int32_t* out4) {
+    if (!out4) VITK_FAIL(VITK_E_ARG, "gemm_nt_w128_plan: null output");
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    if (grid < 8 || (grid & 7)) VITK_FAIL(VITK_E_ARG, "gemm_nt_w128_plan: grid must be a positive multiple of 8 (got %d)", grid);
+    int tm = 0, th = 0;
+    if (M <= 0 || N <= 0 || K <= 0 || !gemm_ntw_plan(M, N, K, grid, &tm, &th)) return 0;
+    out4[0] = tm; out4[1] = th;
+    out4[2] = (int32_t)(1000.0 * gemm_ntw_makespan(N, K, grid, tm, th) + 0.5);
+    // the two-launch split under the same model: its four-wave launch, then the second launch (gemm_ntw_split's constants)
+    const int ts = gemm_ntw_split(M, N, K, grid);
+    const int64_t rest = M - 256LL * ts, tiles_n = N / 256;
+    double old = gemm_ntw_makespan(N, K, grid, ts, 0);
+    if (rest > 0) old += 14.0 / (0.72 * (double)(K / 32) + 6.0) + 0.6 * (double)((((rest + 127) / 128) * tiles_n + grid - 1) / grid);
+    out4[3] = (int32_t)(1000.0 * old + 0.5);
+    return 0;
+}
+
 extern "C" int vitk_gemm_nt_bf16_gelu_bwd_colsum(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
                                                  int64_t M, int64_t N, int64_t K, void* aux, float* colsum_partials, void* stream) {
     if (!colsum_partials) VITK_FAIL(VITK_E_ARG, "gemm_nt_bf16_gelu_bwd_colsum: null partials");
@@ -853,8 +870,10 @@ extern "C" int vitk_gemm_nt_bf16_mul_aux8_colsum(const void* A, int64_t lda, con
     return gemm_nt_impl(A, lda, W, ldw, C, ldc, M, N, K, VITK_EPI_MUL_AUX8, nullptr, nullptr, const_cast<void*>(aux8), colsum_partials, stream);
 }
 
-// ---- the persistent NT kernels: four-wave kernel (gemm_nt_w128.hip) on the full 256-row tiles of whole rounds, 8-wave kernel
-// (gemm_nt_persist.hip) on the remaining rows (the partial last m-tile and what would be a mostly idle last round, as 128-row tiles) ----
+// ---- the persistent NT kernels: four-wave kernel (gemm_nt_w128.hip), 8-wave kernel (gemm_nt_persist.hip) ----
+// Without column sums and fused dropout, and where M % 128 == 0, the four-wave kernel takes ALL rows in one launch: 256-row tiles, then
+// 128-row tiles that fill the last round (gemm_ntw_plan).  Otherwise it takes the 256-row tiles of whole rounds (gemm_ntw_split) and the
+// 8-wave kernel the remaining rows (the partial last m-tile and what would be a mostly idle last round, as 128-row tiles) in a second launch.
 // The row split is a function of (M, N, K) and the CU count only (and of the test switch VITK_NT_W128): vitk_gemm_nt_colsum_rows() reports the
 // partial rows of both launches, and the layout of those rows does NOT depend on vitk_set_cu_reserve() -- a caller that asks for the row
 // count, allocates, and launches while another thread changes the reserve still gets the rows it was promised.  While another
@@ -863,13 +882,16 @@ extern "C" int vitk_gemm_nt_bf16_mul_aux8_colsum(const void* A, int64_t lda, con
 // collective holds), and the 8-wave kernel draws its tiles by dynamic tickets as before.
 // VITK_NT_W128 = bit mask over VITK_EPI_* of the epilogues the four-wave kernel serves (0 = none: the 8-wave kernel alone; unset = NTW_EPIS)
 constexpr unsigned NTW_EPIS = 0xffu;
-static int ntw_tiles_m(const NtpPlan& q, int64_t M, int64_t N, int64_t K, int epilogue, int grid = 0) {
+static bool ntw_enabled(const NtpPlan& q, int64_t M, int64_t N, int64_t K, int epilogue) {
     // (the 8-bit-factor pair follows the switches of its 16-bit twins)
     if (epilogue == VITK_EPI_BIAS_GELU_DG8) epilogue = VITK_EPI_BIAS_GELU_DG;
     if (epilogue == VITK_EPI_MUL_AUX8) epilogue = VITK_EPI_MUL_AUX;
     const char* e = vitk_switch("VITK_NT_W128");
     const unsigned mask = e ? (unsigned)strtoul(e, nullptr, 0) : NTW_EPIS;
-    if (!q.ok || !((mask >> epilogue) & 1u) || !gemm_ntw_serves(M, N, K)) return 0;
+    return q.ok && ((mask >> epilogue) & 1u) && gemm_ntw_serves(M, N, K);
+}
+static int ntw_tiles_m(const NtpPlan& q, int64_t M, int64_t N, int64_t K, int epilogue, int grid = 0) {
+    if (!ntw_enabled(q, M, N, K, epilogue)) return 0;
     return gemm_ntw_split(M, N, K, grid > 0 ? grid : q.grid);
 }
 static int64_t nt_persist_colsum_rows(const NtpPlan& q, int64_t M, int64_t N, int64_t K, int64_t ldc) {
@@ -888,6 +910,13 @@ static int nt_persist_dispatch(const NtpPlan& q, const void* A, int64_t lda, con
     if (grid_w < q.grid / 4) grid_w = q.grid / 4 / 8 * 8;
     // the row split: with column-sum partial rows promised (csum) it is the full-chip one whatever the reserve; otherwise it follows the launch
     // grid (whole rounds of 256 - c workgroups: at N = 768 the full-chip split would leave a third round two thirds empty)
+    const bool colsum_epi = epilogue == VITK_EPI_GELU_BWD || epilogue == VITK_EPI_MUL_AUX || epilogue == VITK_EPI_MUL_AUX8;
+    int tm1 = 0, th1 = 0;
+    if (!colsum_epi && !drop_t && ntw_enabled(q, M, N, K, epilogue) && gemm_ntw_plan(M, N, K, grid_w, &tm1, &th1)) {
+        // one launch on all M rows: no second launch, the last round filled with 128-row tiles
+        if (256LL * (lda > ldw ? lda : ldw) * 2 + K * 2 >= (1LL << 31)) VITK_FAIL(VITK_E_SHAPE, "gemm_nt_bf16: row stride too large (lda %lld, ldw %lld)", (long long)lda, (long long)ldw);
+        return gemm_ntw_launch(tm1, grid_w, A, lda, W, ldw, C, ldc, N, K, epilogue, bias, resid, aux, csum, 0, 0, stream, th1);
+    }
     const int tmw = ntw_tiles_m(q, M, N, K, epilogue == VITK_EPI_GELU_BWD ? VITK_EPI_MUL_AUX : epilogue, csum ? 0 : grid_w);
     const int64_t asz = (epilogue == VITK_EPI_BIAS_GELU_DG8 || epilogue == VITK_EPI_MUL_AUX8) ? 1 : 2;      // bytes per element of aux
     // fused dropout lives in the 8-wave kernel; only the epilogue with column sums has to keep the row split (its partial rows are promised)

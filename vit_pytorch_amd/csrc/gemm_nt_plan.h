@@ -6,7 +6,9 @@
 // height exists because the grid is quantised in rounds of 256 tiles: ViT-B/16 at batch 256 has M = 50,432 rows, i.e. 197
 // m-tiles x 3 n-tiles = 591 tiles for N = 768 = 2.31 rounds that cost 3.  With the last 79 tile-equivalents re-cut into 158
 // half tiles the last round costs half a round.  The plan (how many rows go to the tail) is chosen on the host by
-// evaluating the makespan of the static assignment under a two-parameter cost model.
+// evaluating the makespan of the static assignment under a two-parameter cost model.  The four-wave kernel (gemm_nt_w128.hip) has the
+// same two tile heights and its own plan (gemm_ntw_plan, below); this kernel now serves the column-sum epilogues' remainder rows, fused
+// dropout, M % 128 != 0 and the shapes the four-wave kernel does not take.
 #pragma once
 #include <stdint.h>
 
@@ -28,8 +30,15 @@ int gemm_ntp_launch(const NtpPlan& pl, const void* A, int64_t lda, const void* W
                     int64_t N, int64_t K, int epilogue, const void* bias, const float* resid, void* aux, float* csum, unsigned drop_t, unsigned drop_seed,
                     float inv_keep, void* stream, unsigned drop_m0 = 0);
 
-// the four-wave kernel (gemm_nt_w128.hip): full 256-row tiles only, rows [0, 256 tiles_m); `resid` is f32 (EPI_RESID) or 16-bit (EPI_RESID16)
+// the four-wave kernel (gemm_nt_w128.hip): whole tiles only -- 256-row tiles on rows [0, 256 tiles_m), then 128-row tiles on the next
+// 128 tiles_mh rows (not with the column-sum epilogues); `resid` is f32 (EPI_RESID) or 16-bit (EPI_RESID16).
+//   gemm_ntw_plan:  all M rows in one launch (M % 128 == 0): the two tile counts of least makespan on `grid` workgroups;
+//   gemm_ntw_split: 256-row tiles only, the rest of the rows to the 8-wave kernel (the column-sum epilogues, M % 128 != 0, fused dropout).
 bool gemm_ntw_serves(int64_t M, int64_t N, int64_t K);
 int gemm_ntw_split(int64_t M, int64_t N, int64_t K, int grid);
+bool gemm_ntw_plan(int64_t M, int64_t N, int64_t K, int grid, int* tiles_m, int* tiles_mh);
+double gemm_ntw_half_cost(int64_t K);
+double gemm_ntw_makespan(int64_t N, int64_t K, int grid, int64_t tiles_m, int64_t tiles_mh);
 int gemm_ntw_launch(int tiles_m, int grid, const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
-                    int64_t N, int64_t K, int epilogue, const void* bias, const void* resid, void* aux, float* csum, int abl, int dbg, void* stream);
+                    int64_t N, int64_t K, int epilogue, const void* bias, const void* resid, void* aux, float* csum, int abl, int dbg, void* stream,
+                    int tiles_mh = 0);

@@ -26,6 +26,7 @@
 #include "gemm_nt_plan.h"
 #include "gemm_nt_epi.h"
 #include <stdlib.h>
+#include <algorithm>
 #include <type_traits>
 
 #ifdef VITK_HALF_IS_F16
@@ -65,7 +66,8 @@ struct NtwArgs {
     void* C; long long ldc;
     int M, N, K;
     const __bf16* bias; const void* resid; __bf16* aux; float* csum;
-    int tiles_n, group_n, tiles_m, n_tiles, nt;      // FULL interior tiles only: rows [0, 256 tiles_m), N % 256 == 0
+    int tiles_n, group_n, tiles_m, n_tiles, nt;      // 256-row tiles: rows [0, 256 tiles_m), N % 256 == 0
+    int tiles_mh, n_half;                            // 128-row tiles after them: rows [256 tiles_m, 256 tiles_m + 128 tiles_mh)
     int dbg;            // experiments: bit 0 = skip the epilogue (main loop alone), bit 1 = strict waits after an epilogue,
                         // bits 8..15 = late start of every second workgroup (x s_sleep 127)
 };
@@ -106,18 +108,32 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
 
-    // ---- this workgroup's tiles (gemm_nt_persist.hip's static lists): XCD x owns a contiguous run of the main list and of the tail
-    //      list; its workgroups take every L-th tile of the concatenation ----
+    // ---- this workgroup's tiles (gemm_nt_persist.hip's static lists): XCD x owns a contiguous run of the list of 256-row tiles and of
+    //      the list of 128-row tiles; its workgroups take every L-th tile of the concatenation (the 128-row tiles start on each workgroup
+    //      as soon as its last 256-row tile retires) ----
+    // A 128-row tile is the same K-step stream with half the MFMAs: wave (wm, wn) owns the 64 x 128 wave tile at rows 64 wm, i.e. the
+    // fragment rows f = 0..3 of its usual LDS rows.  The activation DMA puts tile rows 64..127 there (wave 2's pieces, from a descriptor
+    // 64 rows lower); waves 1 and 3 issue their pieces on a range-0 descriptor (no memory traffic), so every K-step keeps its 8 pieces per
+    // wave and every counted wait stays as it is.  The column-sum epilogues (AUX_IN: partial rows per 256-row tile) take 256-row tiles only.
+    constexpr bool HALF_OK = !q_aux_in<EPI>() && ABL == 0;
     const int xcd = blockIdx.x & 7, l0 = blockIdx.x >> 3, L = gridDim.x >> 3;
     const int ms = (int)(((long long)xcd * p.n_tiles) >> 3), count = (int)(((long long)(xcd + 1) * p.n_tiles) >> 3) - ms;
-    if (l0 >= count) return;
+    const int hs = HALF_OK ? (int)(((long long)xcd * p.n_half) >> 3) : 0;
+    const int total = HALF_OK ? count + (int)(((long long)(xcd + 1) * p.n_half) >> 3) - hs : count;
+    if (l0 >= total) return;
     // experiments (p.dbg bits 8..15): every second workgroup of an XCD starts that many s_sleep 127 (~3.4 us each) late, i.e. out of phase
     // with its neighbours -- do epilogue store bursts that fall into other workgroups' main loops pay for the idle start?
     if ((p.dbg >> 8) && (l0 & 1)) { for (int i = (p.dbg >> 8) & 0xff; i > 0; --i) __builtin_amdgcn_s_sleep(127); }
-    auto decode = [&](int idx, int& m0, int& n0, int& mt) {
+    auto decode = [&](int idx, int& m0, int& n0, int& mt) -> bool {      // true: a 128-row tile
         int tn;
-        v_grouped_tile(ms + idx, p.tiles_m, p.tiles_n, p.group_n, mt, tn);
-        m0 = mt * 256; n0 = tn * 256;
+        if (!HALF_OK || idx < count) {
+            v_grouped_tile(ms + idx, p.tiles_m, p.tiles_n, p.group_n, mt, tn);
+            m0 = mt * 256; n0 = tn * 256;
+            return false;
+        }
+        v_grouped_tile(hs + idx - count, p.tiles_mh, p.tiles_n, p.group_n, mt, tn);
+        m0 = 256 * p.tiles_m + 128 * mt; n0 = tn * 256;
+        return true;
     };
 
     // ---- producer: the LDS-DMA stream runs four K-steps ahead of the MFMAs, across tile boundaries ----
@@ -144,16 +160,19 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
     // (AW = 1: the two operands change tile at different K-steps -- the activation stream runs up to three K-step PAIRS ahead, the W stream
     //  four K-steps -- hence one setup per operand; past the end of the tile list the descriptor has range 0)
     auto setup_a = [&](int idx) __attribute__((always_inline)) {
-        if (idx < count) {
+        if (idx < total) {
             int m0, n0, mt;
-            decode(idx, m0, n0, mt);
-            const long long abytes = (255LL * p.lda + p.K) * 2;       // up to the last element of the tile's last row
+            long long abytes = (255LL * p.lda + p.K) * 2;             // up to the last element of the tile's last row
+            if (decode(idx, m0, n0, mt)) {      // 128-row tile: wave 0 rows 0..63, wave 2 rows 64..127 (into LDS rows 128..191), waves 1, 3 nothing
+                m0 -= 64 * (wave >> 1);
+                abytes = (wave & 1) ? 0 : ((64LL * wave + 63) * p.lda + p.K) * 2;
+            }
             a_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + (long long)m0 * p.lda * 2), 0, (int)abytes, 0x00020000);
         } else a_rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0, 0x00020000);
         a_so = 0;
     };
     auto setup_w = [&](int idx) __attribute__((always_inline)) {
-        if (idx < count) {
+        if (idx < total) {
             int m0, n0, mt;
             decode(idx, m0, n0, mt);
             if (p.ldw == 0) {
@@ -242,22 +261,24 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
 #else
 #define V_MFMA32(G, I_, XC, WC) do { } while (0)
 #endif
-#define V_GROUP(G, Z, XC, WC, XN, WN) do { \
-        constexpr int fm_ = (G) >> 1, h_ = ((G) & 1) * 4; \
+// HF: a K-step of a 128-row tile -- 2 MFMAs per group on the activation fragments 0..3; HR: it also skips the reads of the next K-step's
+// activation fragments 4..7 (not where the K-step reads the first fragments of the next tile, which may be a 256-row one)
+#define V_GROUP(G, Z, XC, WC, XN, WN, HF, HR) do { \
+        constexpr int fm_ = (HF) ? (G) >> 2 : (G) >> 1, h_ = (HF) ? ((G) & 3) * 2 : ((G) & 1) * 4; \
         if constexpr (!(ABL & 4) && !(ABL & 8)) v_mfma<Z>(acc[h_ + 0][fm_], XC[fm_], WC[h_ + 0]); \
         V_MFMA32(G, 0, XC, WC); \
-        if constexpr (!(ABL & 2)) { if constexpr ((G) < 8) XN[(G)] = v_rd<(G) * A_FRAG>(rdA); else WN[(G) - 8] = v_rd<((G) - 8) * 1024>(rdW); } \
+        if constexpr (!(ABL & 2)) { if constexpr ((G) < 8) { if constexpr (!((HR) && (G) >= 4)) XN[(G)] = v_rd<(G) * A_FRAG>(rdA); } else WN[(G) - 8] = v_rd<((G) - 8) * 1024>(rdW); } \
         if constexpr (!(ABL & 4) && !(ABL & 8)) v_mfma<Z>(acc[h_ + 1][fm_], XC[fm_], WC[h_ + 1]); \
-        if constexpr (!(ABL & 4) && !(ABL & 8)) v_mfma<Z>(acc[h_ + 2][fm_], XC[fm_], WC[h_ + 2]); \
+        if constexpr (!(ABL & 4) && !(ABL & 8) && !(HF)) v_mfma<Z>(acc[(HF) ? 0 : h_ + 2][fm_], XC[fm_], WC[(HF) ? 0 : h_ + 2]); \
         if constexpr (!(ABL & 1) && ((G) & 1)) { V_PIN(); if constexpr (AW) { if constexpr ((G) < 8) dma_a(dslot_, di0_ + ((G) >> 1)); else dma_w(stg, ((G) >> 1) - 4); } else dma(stg, (G) >> 1); V_PIN(); } \
         V_MFMA32(G, 1, XC, WC); \
-        if constexpr (!(ABL & 4) && !(ABL & 8)) v_mfma<Z>(acc[h_ + 3][fm_], XC[fm_], WC[h_ + 3]); \
+        if constexpr (!(ABL & 4) && !(ABL & 8) && !(HF)) v_mfma<Z>(acc[(HF) ? 0 : h_ + 3][fm_], XC[fm_], WC[(HF) ? 0 : h_ + 3]); \
     } while (0)
     // one K-step.  WAIT = the counted vmcnt statement: own pieces of K-step t + 2 landed (t + 3, t + 4 fly)
     // AW = 1, H = the K-step's place in its pair P.  H = 0: reads the pair's second K-step (slot sp, positions ^ 4), issues the second half of
     // pair P + 2 into slot sp + 2; H = 1: reads the first K-step of pair P + 1 (slot sp + 1), issues the first half of pair P + 3 into slot sp
     // (read by everyone as of the previous barrier).  Either way the W pieces of K-step t + 4 go into stage stg.
-#define V_STEP(Z, XC, WC, XN, WN, WAIT, H) do { \
+#define V_STEP(Z, XC, WC, XN, WN, WAIT, H, HF, HR) do { \
         const unsigned soff_ = ((stg + 1) & 3) * (AW ? V_TILE : V_STAGE); \
         const int sp1_ = sp == 2 ? 0 : sp + 1; \
         const int dslot_ = (H) ? sp : (sp == 0 ? 2 : sp - 1); \
@@ -265,10 +286,10 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
         const unsigned rdA = AW ? ((H) ? a_rd + sp1_ * X_ASLOT : a_rd1 + sp * X_ASLOT) : a_rd + soff_; \
         const unsigned rdW = w_rd + soff_; \
         __builtin_amdgcn_s_setprio(1); \
-        V_GROUP(0, Z, XC, WC, XN, WN); V_GROUP(1, Z, XC, WC, XN, WN); V_GROUP(2, Z, XC, WC, XN, WN); V_GROUP(3, Z, XC, WC, XN, WN); \
-        V_GROUP(4, Z, XC, WC, XN, WN); V_GROUP(5, Z, XC, WC, XN, WN); V_GROUP(6, Z, XC, WC, XN, WN); V_GROUP(7, Z, XC, WC, XN, WN); \
-        V_GROUP(8, Z, XC, WC, XN, WN); V_GROUP(9, Z, XC, WC, XN, WN); V_GROUP(10, Z, XC, WC, XN, WN); V_GROUP(11, Z, XC, WC, XN, WN); \
-        V_GROUP(12, Z, XC, WC, XN, WN); V_GROUP(13, Z, XC, WC, XN, WN); V_GROUP(14, Z, XC, WC, XN, WN); V_GROUP(15, Z, XC, WC, XN, WN); \
+        V_GROUP(0, Z, XC, WC, XN, WN, HF, HR); V_GROUP(1, Z, XC, WC, XN, WN, HF, HR); V_GROUP(2, Z, XC, WC, XN, WN, HF, HR); V_GROUP(3, Z, XC, WC, XN, WN, HF, HR); \
+        V_GROUP(4, Z, XC, WC, XN, WN, HF, HR); V_GROUP(5, Z, XC, WC, XN, WN, HF, HR); V_GROUP(6, Z, XC, WC, XN, WN, HF, HR); V_GROUP(7, Z, XC, WC, XN, WN, HF, HR); \
+        V_GROUP(8, Z, XC, WC, XN, WN, HF, HR); V_GROUP(9, Z, XC, WC, XN, WN, HF, HR); V_GROUP(10, Z, XC, WC, XN, WN, HF, HR); V_GROUP(11, Z, XC, WC, XN, WN, HF, HR); \
+        V_GROUP(12, Z, XC, WC, XN, WN, HF, HR); V_GROUP(13, Z, XC, WC, XN, WN, HF, HR); V_GROUP(14, Z, XC, WC, XN, WN, HF, HR); V_GROUP(15, Z, XC, WC, XN, WN, HF, HR); \
         __builtin_amdgcn_s_setprio(0); \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* the next K-step's fragments are in registers */ \
         if constexpr (!(ABL & 1)) { WAIT; } \
@@ -282,11 +303,13 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
 #define V_WAIT16 asm volatile("s_waitcnt vmcnt(16)" ::: "memory")
     // ---- epilogue of one tile: registers -> global, full lines, stores not waited for ----
     // the 8-wave kernel's, over the wave's two 64-column blocks: "row" r = 2 f + qq covers fragment row f (4 output rows per lane) of
-    // block qq.  Every tile is interior (the launch takes full tiles only), so operand rows come by uncounted asm loads D rows ahead
+    // block qq.  Every tile is interior (the launch takes whole tiles only), so operand rows come by uncounted asm loads D rows ahead
     // and are waited for by exact counts (gemm_nt_epi.h).
     bf16x4 bq[2] = {bf16x4{0, 0, 0, 0}, bf16x4{0, 0, 0, 0}};      // AW = 1: the lane's bias values of the tile, loaded at the tile's first K-step
-    auto epilogue = [&](int m0, int n0, int mt) __attribute__((always_inline)) {
-        constexpr int NR = 16;
+    // HF (a 128-row tile): the wave's fragment rows f = 0..3 only, at rows 64 wm of the tile
+    auto epilogue = [&](int m0, int n0, int mt, auto hc) __attribute__((always_inline)) {
+        constexpr bool HF = decltype(hc)::value;
+        constexpr int NR = HF ? 8 : 16;
 #ifdef NTW_PROBE
         if constexpr (ABL & 8) {
 #pragma unroll
@@ -307,7 +330,7 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(elane));
         int fi = elane & 15, fg = elane >> 4, ewm = wm, ewn = wn;
         asm volatile("" : "+v"(fi), "+v"(fg), "+s"(ewm), "+s"(ewn));
-        const int mrow0 = m0 + ewm * 128 + 4 * fg;              // + 16 f + j
+        const int mrow0 = m0 + ewm * (HF ? 64 : 128) + 4 * fg;  // + 16 f + j
         const int ncolw = n0 + ewn * 128;                       // first column of the wave tile
         const long long obase4 = (long long)mrow0 * p.ldc + ncolw + 4 * fi;      // element (row mrow0, the lane's 4 columns of block 0)
         f32x4 b4[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -359,8 +382,10 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
             };
             row(std::integral_constant<int, 0>{}); row(std::integral_constant<int, 1>{}); row(std::integral_constant<int, 2>{}); row(std::integral_constant<int, 3>{});
             row(std::integral_constant<int, 4>{}); row(std::integral_constant<int, 5>{}); row(std::integral_constant<int, 6>{}); row(std::integral_constant<int, 7>{});
-            row(std::integral_constant<int, 8>{}); row(std::integral_constant<int, 9>{}); row(std::integral_constant<int, 10>{}); row(std::integral_constant<int, 11>{});
-            row(std::integral_constant<int, 12>{}); row(std::integral_constant<int, 13>{}); row(std::integral_constant<int, 14>{}); row(std::integral_constant<int, 15>{});
+            if constexpr (!HF) {
+                row(std::integral_constant<int, 8>{}); row(std::integral_constant<int, 9>{}); row(std::integral_constant<int, 10>{}); row(std::integral_constant<int, 11>{});
+                row(std::integral_constant<int, 12>{}); row(std::integral_constant<int, 13>{}); row(std::integral_constant<int, 14>{}); row(std::integral_constant<int, 15>{});
+            }
         } else if constexpr (EPI == VITK_EPI_RESID16) {
             // the residual epilogue with the stream in the 16-bit type: lane -> (row, 4 columns), 8-byte loads and stores (16 lanes = 128
             // contiguous bytes of a row); the sum is formed in f32 and rounded once
@@ -401,8 +426,10 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
             };
             row(std::integral_constant<int, 0>{}); row(std::integral_constant<int, 1>{}); row(std::integral_constant<int, 2>{}); row(std::integral_constant<int, 3>{});
             row(std::integral_constant<int, 4>{}); row(std::integral_constant<int, 5>{}); row(std::integral_constant<int, 6>{}); row(std::integral_constant<int, 7>{});
-            row(std::integral_constant<int, 8>{}); row(std::integral_constant<int, 9>{}); row(std::integral_constant<int, 10>{}); row(std::integral_constant<int, 11>{});
-            row(std::integral_constant<int, 12>{}); row(std::integral_constant<int, 13>{}); row(std::integral_constant<int, 14>{}); row(std::integral_constant<int, 15>{});
+            if constexpr (!HF) {
+                row(std::integral_constant<int, 8>{}); row(std::integral_constant<int, 9>{}); row(std::integral_constant<int, 10>{}); row(std::integral_constant<int, 11>{});
+                row(std::integral_constant<int, 12>{}); row(std::integral_constant<int, 13>{}); row(std::integral_constant<int, 14>{}); row(std::integral_constant<int, 15>{});
+            }
         } else {
             // after the pair exchange: even lanes own row r = mrow0 + 16 f + 2 pr, odd lanes row r + 1, columns ncol8 .. + 7 of the block
             const int odd = fi & 1;
@@ -496,8 +523,10 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
             };
             frow(std::integral_constant<int, 0>{}); frow(std::integral_constant<int, 1>{}); frow(std::integral_constant<int, 2>{}); frow(std::integral_constant<int, 3>{});
             frow(std::integral_constant<int, 4>{}); frow(std::integral_constant<int, 5>{}); frow(std::integral_constant<int, 6>{}); frow(std::integral_constant<int, 7>{});
-            frow(std::integral_constant<int, 8>{}); frow(std::integral_constant<int, 9>{}); frow(std::integral_constant<int, 10>{}); frow(std::integral_constant<int, 11>{});
-            frow(std::integral_constant<int, 12>{}); frow(std::integral_constant<int, 13>{}); frow(std::integral_constant<int, 14>{}); frow(std::integral_constant<int, 15>{});
+            if constexpr (!HF) {
+                frow(std::integral_constant<int, 8>{}); frow(std::integral_constant<int, 9>{}); frow(std::integral_constant<int, 10>{}); frow(std::integral_constant<int, 11>{});
+                frow(std::integral_constant<int, 12>{}); frow(std::integral_constant<int, 13>{}); frow(std::integral_constant<int, 14>{}); frow(std::integral_constant<int, 15>{});
+            }
             if constexpr (AUX_IN) {
                 if (p.csum) {
                     // bias gradient by-product: the 8 lanes (c ^ 1, 4 row groups) that own the same 8 columns are summed in
@@ -595,7 +624,43 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
         else asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); \
     } while (0)
 
-    for (int idx = l0; idx < count; idx += L) {
+    // the K-steps of one tile (HF: a 128-row tile).  The last K-step reads the next tile's first fragments in full, whatever its form.
+#define V_TILE_STEPS(HF) do { \
+        /* K-steps in pairs (the two fragment sets swap roles); the first K-step writes the accumulators with C = 0 */ \
+        V_STEP(true, xa, wa, xb, wb, V_WAITR, 0, HF, HF); \
+        V_STEP(false, xb, wb, xa, wa, V_WAITR, 1, HF, HF); \
+        if constexpr (AW) { \
+            for (int kt = 2; kt + 6 < p.nt; kt += 2) { \
+                V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0, HF, HF); \
+                V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1, HF, HF); \
+            } \
+            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0, HF, HF);     /* K-step nt - 6: completes the tile's last pair */ \
+            setup_a(idx + L);                                       /* the next three pairs are the next tile's first three ... */ \
+            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1, HF, HF); \
+            setup_w(idx + L);                                       /* ... and the W pieces of the last four K-steps its first four */ \
+            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0, HF, HF); \
+            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1, HF, HF); \
+            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0, HF, HF); \
+            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1, HF, false);  /* reads the NEXT tile's first fragments */ \
+        } else { \
+            for (int kt = 2; kt + 4 < p.nt; kt += 2) { \
+                V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0, HF, HF); \
+                V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1, HF, HF); \
+            } \
+            next_src(idx + L);       /* the pieces of the last four K-steps are the next tile's first four */ \
+            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0, HF, HF); \
+            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1, HF, HF); \
+            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0, HF, HF); \
+            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1, HF, false);  /* reads the NEXT tile's first fragments */ \
+        } \
+        /* the asm MFMAs' results are complete before the compiler's reads of them (it does not see the MFMAs' latency); nothing is \
+           scheduled across the pin */ \
+        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); \
+        V_PIN(); \
+    } while (0)
+    // the 256-row tiles of the list, then (a second loop: the first one's state is dead by then) its 128-row tiles
+    int idx = l0;
+    for (; idx < count; idx += L) {
         int m0, n0, mt;
         decode(idx, m0, n0, mt);
         if constexpr (AW && q_has_bias<EPI>()) {
@@ -605,41 +670,28 @@ __global__ __launch_bounds__(256) void gemm_ntw_kernel(const NtwArgs p) {
                 v_gload_bf16x4(bq[1], bp + 64);
             }
         }
-        // K-steps in pairs (the two fragment sets swap roles); the first K-step writes the accumulators with C = 0
-        V_STEP(true, xa, wa, xb, wb, V_WAITR, 0);
-        V_STEP(false, xb, wb, xa, wa, V_WAITR, 1);
-        if constexpr (AW) {
-            for (int kt = 2; kt + 6 < p.nt; kt += 2) {
-                V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0);
-                V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1);
-            }
-            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0);     // K-step nt - 6: completes the tile's last pair
-            setup_a(idx + L);                               // the next three pairs are the next tile's first three ...
-            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1);
-            setup_w(idx + L);                               // ... and the W pieces of the last four K-steps its first four
-            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0);
-            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1);
-            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0);
-            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1);       // reads the NEXT tile's first fragments
-        } else {
-            for (int kt = 2; kt + 4 < p.nt; kt += 2) {
-                V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0);
-                V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1);
-            }
-            next_src(idx + L);       // the pieces of the last four K-steps are the next tile's first four
-            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0);
-            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1);
-            V_STEP(false, xa, wa, xb, wb, V_WAIT16, 0);
-            V_STEP(false, xb, wb, xa, wa, V_WAIT16, 1);       // reads the NEXT tile's first fragments
-        }
-        // the asm MFMAs' results are complete before the compiler's reads of them (it does not see the MFMAs' latency); nothing is
-        // scheduled across the pin
-        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-        V_PIN();
-        epilogue(m0, n0, mt);
+        V_TILE_STEPS(false);
+        epilogue(m0, n0, mt, std::false_type{});
         relax = (RELAX_OK || (p.dbg & 16)) && !(p.dbg & 3);
     }
+    if constexpr (HALF_OK) {
+        for (; idx < total; idx += L) {
+            int m0, n0, mt;
+            decode(idx, m0, n0, mt);
+            if constexpr (AW && q_has_bias<EPI>()) {
+                if (p.bias) {
+                    const __bf16* bp = p.bias + n0 + wn * 128 + 4 * (lane & 15);
+                    v_gload_bf16x4(bq[0], bp);
+                    v_gload_bf16x4(bq[1], bp + 64);
+                }
+            }
+            V_TILE_STEPS(true);
+            epilogue(m0, n0, mt, std::true_type{});
+            relax = false;          // (VM_RELAX counts the stores of 16 epilogue rows; this one had 8)
+        }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the surplus DMA pieces must not outlive the workgroup's LDS allocation
+#undef V_TILE_STEPS
 #undef V_WAITR
 #undef V_WAIT16
 #undef V_STEP
@@ -655,9 +707,11 @@ int v_set_max_lds(Kern kernel, int bytes) {
 }  // namespace
 
 // Shapes the four-wave kernel takes: K-steps in pairs with a peeled first pair and four peeled last steps (K % 64 == 0, K >= 256), whole
-// 256-column tiles (N % 256 == 0), 32-bit descriptor offsets.  It computes FULL 256-row tiles only, rows [0, 256 tiles_m): the caller
-// (gemm_bf16.hip) gives the remaining rows -- a partial last m-tile, and the rows of a mostly idle last round, which the 8-wave kernel
-// cuts into 128-row tiles -- to the 8-wave kernel in a second launch.
+// 256-column tiles (N % 256 == 0), 32-bit descriptor offsets.  It computes whole tiles only: 256-row tiles on rows [0, 256 tiles_m), then
+// 128-row tiles on the next 128 tiles_mh rows.  Where M % 128 == 0, gemm_ntw_plan() cuts all M rows into the two heights for ONE launch
+// (the 128-row tiles fill the last round).  Otherwise, and for the column-sum epilogues (whose partial rows are promised per 256-row
+// tile), gemm_ntw_split() picks the 256-row tiles and the caller (gemm_bf16.hip) gives the remaining rows to the 8-wave kernel in a
+// second launch.
 bool gemm_ntw_serves(int64_t M, int64_t N, int64_t K) {
     return !((K % 64) || K < 256 || (N % 256) || M < 256 || N > 16128 || (K / 32) * (long long)V_TILE >= (1LL << 31));
 }
@@ -692,13 +746,53 @@ int gemm_ntw_split(int64_t M, int64_t N, int64_t K, int grid) {
     return (int)best_tm;
 }
 
+// One launch on all M rows (M % 128 == 0): tiles_m 256-row tiles, then tiles_mh 128-row tiles, chosen to minimise the makespan of the
+// static per-XCD tile lists on `grid` workgroups.  Cost of a 128-row tile in units of a 256-row one: h = (0.41 nt + 4.2) / (0.72 nt + 6)
+// (nt = K / 32; the 256-row tile's cost is gemm_ntw_split's) [measured, tools/nt_probe, the four-wave kernel on all rows as 128-row tiles
+// against all rows as 256-row tiles, M = 50,432: K = 768 0.56-0.68 by epilogue (model 0.60), K = 2304 0.58, K = 3072 0.56-0.59 (0.575)].  Makespan of a plan: per XCD, c 256-row and hc 128-row tiles dealt to L = grid / 8 workgroups
+// in turn, 256-row tiles first -- the workgroups at positions >= c % L have one 256-row tile fewer and get the 128-row tiles first.
+double gemm_ntw_half_cost(int64_t K) {
+    const double nt = (double)(K / 32);
+    return (0.41 * nt + 4.2) / (0.72 * nt + 6.0);
+}
+double gemm_ntw_makespan(int64_t N, int64_t K, int grid, int64_t tiles_m, int64_t tiles_mh) {
+    const long long tiles_n = N / 256, nf = tiles_m * tiles_n, nh = tiles_mh * tiles_n, L = grid / 8;
+    const double h = gemm_ntw_half_cost(K);
+    double worst = 0.0;
+    for (long long x = 0; x < 8; ++x) {
+        const long long c = ((x + 1) * nf >> 3) - (x * nf >> 3), hc = ((x + 1) * nh >> 3) - (x * nh >> 3);
+        const long long q = c / L, r = c % L, hq = hc / L, hr = hc % L;
+        double w = (double)q + h * (double)(hq + (hr > 0 ? 1 : 0));                             // workgroups r .. L - 1
+        if (r > 0) w = std::max(w, (double)(q + 1) + h * (double)(hq + (hr > L - r ? 1 : 0)));  // workgroups 0 .. r - 1
+        worst = std::max(worst, w);
+    }
+    return worst;
+}
+bool gemm_ntw_plan(int64_t M, int64_t N, int64_t K, int grid, int* tiles_m, int* tiles_mh) {
+    *tiles_m = 0; *tiles_mh = 0;
+    if (M % 128 || !gemm_ntw_serves(M, N, K) || grid < 8) return false;
+    const long long tiles_n = N / 256, units = M / 128, tm_all = units / 2;
+    // converting more than one round of 256-row tiles into 128-row pairs cannot shorten the last round: candidates tm_all - g .. tm_all
+    const long long lo = std::max(0LL, tm_all - (grid + tiles_n - 1) / tiles_n - 1);
+    long long best_tm = tm_all;
+    double best = gemm_ntw_makespan(N, K, grid, tm_all, units - 2 * tm_all);
+    for (long long tm = tm_all - 1; tm >= lo; --tm) {
+        const double c = gemm_ntw_makespan(N, K, grid, tm, units - 2 * tm);
+        if (c < best - 1e-9) { best = c; best_tm = tm; }
+    }
+    *tiles_m = (int)best_tm; *tiles_mh = (int)(units - 2 * best_tm);
+    return true;
+}
+
 int gemm_ntw_launch(int tiles_m, int grid, const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
-                    int64_t N, int64_t K, int epilogue, const void* bias, const void* resid, void* aux, float* csum, int abl, int dbg, void* stream) {
+                    int64_t N, int64_t K, int epilogue, const void* bias, const void* resid, void* aux, float* csum, int abl, int dbg, void* stream,
+                    int tiles_mh) {
     NtwArgs a;
     a.A = (const char*)A; a.lda = lda; a.W = (const char*)W; a.ldw = ldw; a.C = C; a.ldc = ldc;
-    a.M = 256 * tiles_m; a.N = (int)N; a.K = (int)K;
+    a.M = 256 * tiles_m + 128 * tiles_mh; a.N = (int)N; a.K = (int)K;
     a.bias = (const __bf16*)bias; a.resid = resid; a.aux = (__bf16*)aux; a.csum = csum;
     a.tiles_n = (int)(N / 256); a.tiles_m = tiles_m; a.n_tiles = a.tiles_m * a.tiles_n; a.nt = (int)(K / 32);
+    a.tiles_mh = tiles_mh; a.n_half = tiles_mh * a.tiles_n;
     // grouped tile order (the 8-wave kernel's scheme): one group up to 8 n-tiles, beyond that groups of 4 (K <= 768) or balanced groups of <= 6; n fastest inside a group
     // [measured on the whole step, round 5, two boxes x 2-3 interleaved runs (profiles/r05g_group_sweep.log): groups of 4 n-tiles for the
     //  9- and 12-tile shapes (QKV, FF1, dFF1) 30.83 ms against 30.97 with the 8-wave kernel's balanced groups of <= 6; 3: 31.05; 9 / 12: level]
@@ -711,7 +805,9 @@ int gemm_ntw_launch(int tiles_m, int grid, const void* A, int64_t lda, const voi
     if (const char* e = vitk_exp("VITK_NTW_RELAX")) a.dbg |= e[0] == 'a' ? 16 : (e[0] == 'n' ? 2 : 0);      // A/B: all / none
     const int lds_bytes = V_RING + a.tiles_n * 512 + 16;
     hipStream_t st = (hipStream_t)stream;
-    if (tiles_m <= 0 || grid < 8) VITK_FAIL(VITK_E_ARG, "gemm_nt_bf16 (w128): nothing to do");
+    if (tiles_m < 0 || tiles_mh < 0 || tiles_m + tiles_mh <= 0 || grid < 8) VITK_FAIL(VITK_E_ARG, "gemm_nt_bf16 (w128): nothing to do");
+    if (tiles_mh > 0 && (abl || epilogue == VITK_EPI_GELU_BWD || epilogue == VITK_EPI_MUL_AUX || epilogue == VITK_EPI_MUL_AUX8))
+        VITK_FAIL(VITK_E_ARG, "gemm_nt_bf16 (w128): 128-row tiles exist without column sums and ablations only");
     // the activation feed: 128-byte rows (round 6) unless VITK_NTW_A128=0 asks for round 5's 64-byte pieces (the same-box A/B of the two feeds)
     const char* aw_e = vitk_switch("VITK_NTW_A128");
     const bool a128 = !(aw_e && aw_e[0] == '0');
